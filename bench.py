@@ -7,11 +7,15 @@ in HBM.  N GPUs = N ranks (torch.distributed over RCCL), each processing its own
 documents (weak scaling: docs per GPU fixed).  The only collectives are the max of the elapsed time
 and the sum of the per-rank stats.
 
-Prints ONE JSON line (rank 0) with value = whole-job merged-update input GB/s, plus docs/s, the
+Prints ONE JSON line (rank 0) with value = whole-job merged-update input GB/s, plus docs/s and the
 roofline of the dominant kernel (the LDS fast-path merge, algorithmic bytes = sum of input + output
-bytes of its documents, timed with HIP events on the call's stream) and the CPU baseline (the C
-restatement in oracle/ -- a faithful port of yjs 13.5.16's algorithm -- on a bounded sample, timed on
-the host cores of the same box).
+bytes of its documents, timed with HIP events on the call's stream).  A plain run sets up, warms up,
+times the steps and prints that line; --dump-outputs DIR also writes what the last timed step computed.
+
+--full adds the measurements that take runs of their own: the host-resident (PCIe-inclusive) path
+before and after the device-resident steps, the CPU baseline (the C restatement in oracle/ -- a
+faithful port of yjs 13.5.16's algorithm -- on a bounded sample, timed on the host cores of the same
+box) and the secondary workload lines.
 """
 import argparse
 import json
@@ -45,8 +49,16 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--workload", default="c2", choices=sorted(WORKLOADS))
     p.add_argument("--docs-per-gpu", type=int, default=10000)
+    p.add_argument("--full", action="store_true",
+                   help="also measure the host-resident (PCIe-inclusive) path, the CPU baseline and the "
+                        "secondary workload lines (pcie_inclusive, cpu_baseline, secondary in the result line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy: "
+                        "doc_status and doc_len (float64, one entry per document) and doc_bytes (float32: the "
+                        "output bytes of the documents listed in doc_sample, packed in document order; every "
+                        "document unless that would exceed the size budget, else a fixed seeded sample)")
     p.add_argument("--cpu-baseline-seconds", type=float, default=10.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--partition", default="auto", choices=["auto", "hash", "bytes"],
                    help="document -> rank assignment: hash32(docIndex) % N, or greedy byte balance "
                         "(auto: hash for the small-document workloads, bytes for C3 / C5)")
@@ -61,7 +73,7 @@ def parse():
                         "complete every document with the bytes of ym_merge; sync: one ym_merge call per "
                         "step (host waits for each); auto: async when the verification passes")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the secondary workload lines (C4/C2-V2/C4-V2 merges, C3 diff/sv)")
+                   help="with --full: skip the secondary workload lines (C4/C2-V2/C4-V2 merges, C3 diff/sv)")
     return p.parse_args()
 
 
@@ -376,6 +388,7 @@ class StubEngine:
 
         def call():
             o_arena[:n].copy_(g_arena)
+            o_off.copy_(g_off[g_doc[:-1].long()])
             o_len.copy_(lens)
             o_st.zero_()
             return 0, n
@@ -432,6 +445,42 @@ def pcie_inclusive(eng, arena, upd_off, doc_upd, fmt, in_bytes):
     return res
 
 
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # of .npy payload per --dump-outputs directory (64 MB with headroom)
+
+
+def dump_outputs(path, o_arena, o_off, o_len, o_st, suffix=""):
+    """--dump-outputs: what a caller of the timed merge receives, one document per entry: its status, the
+    length of its merged update (0 when the status is an error) and the update's bytes.  The arena offsets are
+    not written: they say where a document landed in the output arena (some paths allocate with an atomic
+    counter, so the order may differ from run to run), not what was computed -- the bytes are packed in
+    document order instead.  float64 holds every status / length exactly, float32 every byte."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    nd = int(o_st.numel())
+    st = o_st.to("cpu").numpy().astype(np.int64)
+    ln = np.where(st == 0, o_len.to("cpu").numpy().astype(np.int64), 0)
+    # the documents whose bytes are written: all of them, or -- above the budget -- the longest prefix of a
+    # seeded permutation that fits (the same documents in every run with the same arguments)
+    budget = max(0, DUMP_BUDGET_BYTES - 24 * nd) // 4
+    sample = np.arange(nd, dtype=np.int64)
+    if int(ln.sum()) > budget:
+        perm = np.random.default_rng(20240229).permutation(nd)
+        keep = int(np.searchsorted(np.cumsum(ln[perm]), budget, side="right"))
+        sample = np.sort(perm[:keep]).astype(np.int64)
+    lens = torch.from_numpy(ln[sample]).to(o_arena.device)
+    total = int(lens.sum().item())
+    if total:
+        first = torch.cumsum(lens, 0) - lens  # where each document starts in the packed array
+        src0 = o_off.to(torch.int64)[torch.from_numpy(sample).to(o_arena.device)]
+        idx = torch.repeat_interleave(src0 - first, lens) + torch.arange(total, device=o_arena.device)
+        packed = o_arena[idx].to("cpu").numpy()
+    else:
+        packed = np.zeros(0, dtype=np.uint8)
+    for name, arr in (("doc_status", st.astype(np.float64)), ("doc_len", ln.astype(np.float64)),
+                      ("doc_sample", sample.astype(np.float64)), ("doc_bytes", packed.astype(np.float32))):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), arr)
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -477,12 +526,14 @@ def main():
     else:
         from yjs_amd import Engine
         eng = Engine(local)
-    # the host-resident path (the Node addon's), measured first -- its staging buffers and page-locked pool are
+    # --full: the host-resident path (the Node addon's), measured first -- its staging buffers and page-locked pool are
     # then allocated before the device-resident sets, as in a serving process that only takes host batches --
     # and again after the device-resident steps (pcie_inclusive.after_device_resident_steps).  Measured only
     # after them, i.e. allocated after the rotated sets' ~1 GB, the pipelined call took 1.19 ms instead of 0.80
     # (the cause is not pinned down)
-    pcie_early = pcie_inclusive(eng, arena, upd_off, doc_upd, fmt, in_bytes) if world == 1 and not stub else None
+    pcie_early = None
+    if args.full and world == 1 and not stub:
+        pcie_early = pcie_inclusive(eng, arena, upd_off, doc_upd, fmt, in_bytes)
     # u32 offsets (YM_OFF32) when the rank's arena is below 4 GiB: half the offset bytes per update
     off32 = in_bytes < 2 ** 32
     cap = 4 * in_bytes + 128 * n_docs + 8192  # fast-path slots (2*in + 64 per doc) + general-path room
@@ -612,6 +663,12 @@ def main():
             dist.barrier()
         elapsed = time.perf_counter() - t0
 
+    if args.dump_outputs:
+        # the output arrays of the buffer set the last timed step wrote (step k uses set k % rot)
+        last = sets[(max(args.steps, 1) - 1) % rot][1]
+        sync()
+        dump_outputs(args.dump_outputs, *last[3:], suffix=f".rank{rank}" if world > 1 else "")
+
     # the only collectives: max of the timed region, sum of per-rank counters (RCCL over xGMI)
     from yjs_amd.distributed import reduce_run
     elapsed, (in_all, out_all, docs_all, err_all, fast_all, gen_all, upd_all) = reduce_run(
@@ -677,13 +734,13 @@ def main():
         }
         if stub:
             line["stub"] = "cpu-stub: launcher/sharding/reduce plumbing only, no merge computed"
-        if world == 1 and not stub:
+        if args.full and world == 1 and not stub:
             late = pcie_inclusive(eng, arena, upd_off, doc_upd, fmt, in_bytes)
             line["pcie_inclusive"] = dict(pcie_early, after_device_resident_steps={
                 k: late[k] for k in ("value", "ms_per_call", "mean_ms_per_call", "bytes_match_unpipelined")})
-        if not args.no_cpu_baseline and world == 1 and not stub:  # the host baseline: N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub:  # the host baseline: N = 1 only
             line["cpu_baseline"] = cpu_baseline(arena, upd_off, doc_upd, fmt, args.cpu_baseline_seconds)
-        if not args.no_secondary and world == 1 and not stub:
+        if args.full and not args.no_secondary and world == 1 and not stub:
             line["secondary"] = secondary(dev, eng)
         print(json.dumps(line), flush=True)
     if world > 1:

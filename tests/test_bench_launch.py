@@ -47,6 +47,54 @@ def test_bench_launches_two_ranks(partition):
     assert partition in line["config"]["parallelism"]
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs writes the documents of the last timed step (here the stub's copies of its inputs) as
+    float32 / float64 .npy arrays, the same from run to run; a plain run carries none of --full's objects."""
+    D = 48
+    dumps = []
+    for k in range(2):
+        line = _run_bench("--docs-per-gpu", str(D), "--dump-outputs", str(tmp_path / f"d{k}"))
+        assert line["steps"] == 2 and line["ms_per_step"] > 0
+        assert not {"pcie_inclusive", "cpu_baseline", "secondary"} & set(line)
+        dumps.append({p.name: np.load(p) for p in sorted((tmp_path / f"d{k}").iterdir())})
+    assert sorted(dumps[0]) == ["doc_bytes.npy", "doc_len.npy", "doc_sample.npy", "doc_status.npy"]
+    for name, arr in dumps[0].items():
+        assert arr.dtype == (np.float32 if name == "doc_bytes.npy" else np.float64), name
+        assert np.array_equal(arr, dumps[1][name]), name
+    a, o, d = load_ymb("c2_v1")
+    assert (dumps[0]["doc_status.npy"] == 0).all()
+    assert np.array_equal(dumps[0]["doc_sample.npy"], np.arange(D))
+    assert np.array_equal(dumps[0]["doc_len.npy"], doc_sizes(o, d)[:D])
+    assert np.array_equal(dumps[0]["doc_bytes.npy"].astype(np.uint8), a[:int(o[d[D]])])
+
+
+def test_bench_dump_outputs_sample_fits_budget(tmp_path, monkeypatch):
+    """Above the size budget the bytes of a seeded sample of the documents are written: the same documents on
+    every call, whole, in document order, within the budget."""
+    import torch
+    import bench
+    a, o, d = load_ymb("c2_v1")
+    D = 40
+    sizes = doc_sizes(o, d)[:D]
+    starts = o[d[:D]].astype(np.int64)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 24 * D + 4 * int(sizes.sum()) // 3)
+    st = np.zeros(D, dtype=np.int32)
+    st[7] = 3  # a failed document has no bytes, whatever its length entry holds
+    args = (torch.from_numpy(a[:int(o[d[D]])].copy()), torch.from_numpy(starts), torch.from_numpy(sizes.astype(np.int64)),
+            torch.from_numpy(st))
+    bench.dump_outputs(str(tmp_path / "x"), *args)
+    bench.dump_outputs(str(tmp_path / "y"), *args)
+    x = {n: np.load(tmp_path / "x" / f"{n}.npy") for n in ("doc_status", "doc_len", "doc_sample", "doc_bytes")}
+    for n, arr in x.items():
+        assert np.array_equal(arr, np.load(tmp_path / "y" / f"{n}.npy")), n
+    sample = x["doc_sample"].astype(np.int64)
+    assert 0 < len(sample) < D and (np.diff(sample) > 0).all()
+    assert x["doc_len"][7] == 0 and x["doc_status"][7] == 3
+    assert sum(arr.nbytes for arr in x.values()) <= 24 * D + 4 * int(sizes.sum()) // 3
+    want = np.concatenate([a[starts[i]:starts[i] + sizes[i]] for i in sample if i != 7])
+    assert np.array_equal(x["doc_bytes"].astype(np.uint8), want)
+
+
 def test_hash_partition_rule_and_cover():
     ids = np.arange(1000)
     shards = hash_partition(ids, 4)

@@ -5,18 +5,19 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 T=${TAG:-sec}
-mkdir -p gpurun_out/$T
+OUT=${OUT:-bench_out}  # where the logs and result lines go
+mkdir -p $OUT/$T
 [ -n "$LIB" ] && export YMERGE_LIB=$PWD/$LIB
-YM_SECONDARY="$SEC" timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/$T/bench.json 2> gpurun_out/$T/bench.err || { tail -20 gpurun_out/$T/bench.err; exit 1; }
-python3 - gpurun_out/$T/bench.json <<'PY'
+YM_SECONDARY="$SEC" timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $OUT/$T/bench.json 2> $OUT/$T/bench.err || { tail -20 $OUT/$T/bench.err; exit 1; }
+python3 - $OUT/$T/bench.json <<'PY'
 import json, sys
 r = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 for k, v in r.get("secondary", {}).items():
     print(f"{k:22s} " + json.dumps({x: v[x] for x in v if x in ('ms_per_step', 'kernel_ms', 'docs_fast', 'docs_large', 'docs_general', 'error')} if isinstance(v, dict) else v))
 PY
 if [ -n "$PROF" ]; then
-  YM_SECONDARY="$SEC" timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/$T/prof -o run -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > /dev/null 2>&1 || exit 1
-  python3 - gpurun_out/$T/prof <<'PY'
+  YM_SECONDARY="$SEC" timeout -s KILL 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/$T/prof -o run -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > /dev/null 2>&1 || exit 1
+  python3 - $OUT/$T/prof <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_stats.csv", recursive=True)[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: -float(r["TotalDurationNs"]))

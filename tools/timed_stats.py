@@ -1,7 +1,7 @@
 """Average duration of the headline kernel's timed launches in a rocprofv3 kernel trace of
-`bench.py --no-secondary --no-cpu-baseline` (default 50 steps): the STEPS full-grid launches right before the
-last run of launches of another grid (the host-path measurement after the timed region; bench.py also measures
-that path first, before the device-resident steps).
+`bench.py` (default 50 steps): the last STEPS launches of the longest run of full-grid launches.  In a plain run
+those are the last of the trace; with `--full` launches of other grids follow (the host-path measurement after
+the timed region; bench.py --full also measures that path first, before the device-resident steps).
 Usage: python tools/timed_stats.py <run_kernel_trace.csv> [steps]"""
 import csv
 import statistics
