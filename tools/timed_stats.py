@@ -9,7 +9,9 @@ import sys
 
 path = sys.argv[1]
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
-rows = sorted((r for r in csv.DictReader(open(path)) if "k_fast_merge_v1<0, 8" in r["Kernel_Name"]),
+# (the one-wave kernel, or the two-wave one: whichever the run launched)
+rows = sorted((r for r in csv.DictReader(open(path))
+               if "k_fast_merge_v1<0, 8" in r["Kernel_Name"] or "k_fast_merge_v1_split" in r["Kernel_Name"]),
               key=lambda r: int(r["Start_Timestamp"]))
 full = max(int(r["Grid_Size_X"]) for r in rows)  # the whole batch in one launch
 # the longest run of whole-batch launches is the device-resident phase (verification, warmup, timed steps);

@@ -30,6 +30,10 @@
 // checks), so the fast path needs no global atomics; the general path appends after that region.
 // Documents are mapped to blocks XCD-contiguously (block b runs on XCD b % 8): neighbouring documents
 // share their boundary cache lines (input bytes, offsets, per-document results) inside one L2.
+// The hot V1 merge (OP_MERGE, one block per document) runs as a two-wave workgroup by default
+// (k_fast_merge_v1_split: phases 2-4 in wave 0, the delete set's walk and phase 5 in wave 1, at the same time;
+// MapSplit, merge_doc_v1_split); the one-wave kernel serves every other form (delete-set merges, the retry
+// pass, the grid-stride loop, the ablation builds) and YMERGE_FAST_SPLIT=0.
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
 
@@ -97,6 +101,55 @@ struct Map {
   static_assert(L_PLAST + 2 * SEC <= L_SB, "part arrays fit over the clock lengths");
   static_assert(L_UORD + UPD <= L_END, "walk lists fit in the record region");
 };
+// The two-wave hot kernel (k_fast_merge_v1_split): wave 0 runs the struct half and wave 1 the delete-set half
+// of one document at the same time, so nothing is overlaid: the delete ranges and the merge arrays have LDS of
+// their own next to the section records and the document bytes (which wave 0 still reads while it writes the
+// struct section).  10,240 B per two-wave workgroup = 16 workgroups per CU, the same 8 waves per SIMD.
+struct MapSplit {
+  static constexpr uint32_t IN = IN_HOT;
+  static constexpr uint32_t L_IN = 0;                    // u8[IN + 16]
+  static constexpr uint32_t L_UOFF = IN + 16;            // u16[UPD + 1]
+  static constexpr uint32_t L_MISC = L_UOFF + 272;       // u32[4]   counters: sections, delete ranges, deferred strings,
+                                                         //          updates with structs and a delete set to walk
+  static constexpr uint32_t L_DUP = L_MISC + 16;         // u32[4]
+  static constexpr uint32_t L_HIST = L_DUP + 16;         // u32[16]  deferred strings (rstr_defer)
+  static constexpr uint32_t L_UDS = L_HIST + 64;         // u16[UPD]
+  static constexpr uint32_t L_PUB = L_UDS + 2 * UPD;     // u32[3]   wave 0's verdict (SP_*), hdr, struct_bytes (barrier B)
+  static constexpr uint32_t L_W1BAD = L_PUB + 12;        // u32      a struct walk declined (either wave; barrier A)
+  static constexpr uint32_t L_TAB = L_PUB + 16;          // u32[4]   per wave: its updates with structs | delete-only
+                                                         //          updates to walk << 8 | an empty update << 16 (S2)
+  static constexpr uint32_t L_UORD = L_TAB + 16;         // u8[UPD]  updates with structs: those of updates [0, 64)
+                                                         //          from 0, those of updates [64, 128) from 64
+  static constexpr uint32_t L_UORD2 = L_UORD + UPD;      // u8[UPD]  delete-only updates whose delete set has clients,
+                                                         //          in the same two halves
+  static constexpr uint32_t L_UORD3 = L_UORD2 + UPD;     // u8[UPD]  updates with structs whose delete set has clients
+  // wave 0: client sections
+  static constexpr uint32_t L_SKEY = L_UORD3 + UPD;      // u64[SEC]
+  static constexpr uint32_t L_SLN = L_SKEY + 8 * SEC;    // u32[SEC]
+  static constexpr uint32_t L_SB = L_SLN + 4 * SEC;      // u16[SEC]
+  static constexpr uint32_t L_SE = L_SB + 2 * SEC;       // u16[SEC]
+  static constexpr uint32_t L_PFIRST = L_SLN;            // u16[SEC]  (over the clock lengths, as in Map)
+  static constexpr uint32_t L_PLAST = L_SLN + 2 * SEC;   // u16[SEC]
+  // wave 1: delete ranges, merged ranges, groups
+  static constexpr uint32_t L_DKEY = L_SE + 2 * SEC;     // u64[DSN]
+  static constexpr uint32_t L_DLEN = L_DKEY + 8 * DSN;   // u32[DSN]
+  static constexpr uint32_t L_DSEQ = L_DLEN + 4 * DSN;   // u16[DSN]
+  static constexpr uint32_t L_QCLK = L_DSEQ + 2 * DSN;   // u32[DSN]
+  static constexpr uint32_t L_QEND = L_QCLK + 4 * DSN;   // u32[DSN]
+  static constexpr uint32_t L_QGRP = L_QEND + 4 * DSN;   // u8[DSN]
+  static constexpr uint32_t L_QPRE = L_QGRP + DSN;       // u16[DSN + 1]
+  static constexpr uint32_t L_GFIRST = L_QPRE + 272;     // u16[DSN + 1]
+  static constexpr uint32_t L_GCLI = L_GFIRST + 272;     // u32[DSN]
+  static constexpr uint32_t L_GMIN = L_GCLI + 4 * DSN;   // u32[DSN]
+  static constexpr uint32_t L_GBYR = L_DKEY;             // u16[DSN]  (over the sorted keys, as in Map)
+  static constexpr uint32_t L_GB2 = L_DKEY + 512;        // u32[DSN]
+  static constexpr uint32_t LDS_BYTES = 10240;
+  static_assert(L_GMIN + 4 * DSN <= LDS_BYTES, "the map fits its workgroup's share");
+  static_assert(L_SKEY % 16 == 0 && L_DKEY % 16 == 0 && L_QCLK % 16 == 0, "16-aligned arrays");
+  static_assert(L_GB2 + 4 * DSN <= L_DSEQ + 2 * DSN && L_GB2 >= L_GBYR + 2 * DSN, "rank arrays fit over the sorted keys");
+  static_assert(L_PLAST + 2 * SEC <= L_SB, "part arrays fit over the clock lengths");
+};
+static_assert(MapSplit::LDS_BYTES * 16 <= 160 * 1024, "8 waves per SIMD: 16 two-wave workgroups per CU (160 KB LDS)");
 using MapHot = Map<IN_HOT>;
 using MapNested = Map<IN_NESTED>;
 static_assert(MapHot::LDS_BYTES * 32 <= 160 * 1024, "8 one-wave workgroups per SIMD (160 KB LDS per CU)");
@@ -236,8 +289,10 @@ __device__ __forceinline__ bool item_fast(Cur &c, uint32_t info, uint32_t &len) 
 // the parentSub bit get the bit cleared in place (13.5.16's lazy reader reads parentSub only without
 // origins and writes the info byte back without it, E8), so sections copy verbatim afterwards.
 // Returns false to decline.  NESTED: nested payloads (any objects / arrays, JSON texts) are checked too
-// (the retry pass over the documents the hot kernel declined; ym_canon_chk.h).
-template <class M, bool NESTED = false>
+// (the retry pass over the documents the hot kernel declined; ym_canon_chk.h).  LIST (the two-wave kernel): an
+// update whose delete set has clients (or is missing) is appended to the walk list M::L_UORD3 (count at
+// M::L_MISC + 12) for the delete-set wave.
+template <class M, bool NESTED = false, bool LIST = false>
 __device__ __forceinline__ bool walk_sections(uint32_t u) {
   Cur c = {at<uint16_t>(M::L_UOFF + 2 * u), at<uint16_t>(M::L_UOFF + 2 * u + 2), false};
   const uint32_t nclients = rvu(c);
@@ -273,6 +328,9 @@ __device__ __forceinline__ bool walk_sections(uint32_t u) {
     }
   }
   at<uint16_t>(M::L_UDS + 2 * u) = (uint16_t)c.p;
+  if constexpr (LIST) {
+    if (!c.bad && (c.p >= c.e || sm[c.p] != 0)) at<uint8_t>(M::L_UORD3 + atomicAdd(&at<uint32_t>(M::L_MISC + 12), 1u)) = (uint8_t)u;
+  }
   return !c.bad;
 }
 // Walks the delete set of update u (DeleteSet.js:219-256) and appends its ranges (slots from misc[1]);
@@ -341,8 +399,11 @@ __device__ unsigned g_fast_ph[131072][8];  // per block: s_memrealtime (low 32 b
   }
 
 // ---- 3/4. client sections of document d: rank sort, layout, struct section written (EE per lane) -------
+// SPLIT (the two-wave kernel, this is wave 0): syncs are wave-local; once the layout has passed every check the
+// verdict, `hdr` and `struct_bytes` are published at M::L_PUB and the workgroup's barrier B is taken here,
+// before the bytes are written (SP_DONE: barrier taken; any other result: the caller publishes and takes it).
 enum : int { SP_DONE = 0, SP_DECLINE = 1, SP_STOP = 2, SP_CAP = 3 };
-template <class M, uint32_t EE, int STOP>
+template <class M, uint32_t EE, int STOP, bool SPLIT = false>
 __device__ __forceinline__ int sec_phase(const GeneralJob &j, uint32_t d, uint32_t nsec, uint64_t slot, uint64_t slot_al,
                                          uint64_t slot_end, uint64_t bytes, Slot dst, uint32_t &hdr, uint32_t &struct_bytes) {
   const uint32_t lane = threadIdx.x;
@@ -391,7 +452,7 @@ __device__ __forceinline__ int sec_phase(const GeneralJob &j, uint32_t d, uint32
       }
     }
     if (!ranked) rank_le4(M::L_SKEY, nsec, rk, rr);
-    __syncthreads();
+    lds_sync<SPLIT>();
 #pragma unroll
     for (uint32_t s = 0; s < EE; s++) {
       const uint32_t i = lane + 64 * s;
@@ -404,7 +465,7 @@ __device__ __forceinline__ int sec_phase(const GeneralJob &j, uint32_t d, uint32
         atomicOr(&at<uint32_t>(M::L_DUP + 4 * (r >> 5)), 1u << (r & 31));
       }
     }
-    __syncthreads();
+    lds_sync<SPLIT>();
     {
       // equal (client, clock) keys share a rank: the ranks seen must be all nsec of them (else overlapping
       // inputs)
@@ -463,7 +524,7 @@ __device__ __forceinline__ int sec_phase(const GeneralJob &j, uint32_t d, uint32
         if (plastf[s]) at<uint16_t>(M::L_PLAST + 2 * pid) = (uint16_t)(run & 0xffff);
       }
     }
-    __syncthreads();
+    lds_sync<SPLIT>();
     uint32_t runu[EE], soff[EE], sbytes_lane = 0;
 #pragma unroll
     for (uint32_t s = 0; s < EE; s++) {
@@ -490,6 +551,14 @@ __device__ __forceinline__ int sec_phase(const GeneralJob &j, uint32_t d, uint32
       if (slot_al + hdr + struct_bytes > slot + 2 * bytes + 64) return SP_DECLINE;
       if (lane == 0) { j.status[d] = ym::ST_CAPACITY; j.out_len[d] = 0; }  // caller's arena too small
       return SP_CAP;
+    }
+    if constexpr (SPLIT) {
+      if (lane == 0) {
+        at<uint32_t>(M::L_PUB) = SP_DONE;
+        at<uint32_t>(M::L_PUB + 4) = hdr;
+        at<uint32_t>(M::L_PUB + 8) = struct_bytes;
+      }
+      __syncthreads();  // barrier B
     }
     YM_TS(3)
     if (STOP == 4) return SP_STOP;
@@ -518,11 +587,15 @@ __device__ __forceinline__ int sec_phase(const GeneralJob &j, uint32_t d, uint32
 }
 
 // ---- 5/6. delete set of document d (EE delete ranges per lane: 1 when they fit one wave) --------------
-enum : int { DS_DONE = 0, DS_DECLINE = 1, DS_STOP = 2 };
-template <class M, uint32_t EE, int STOP, bool DSV2>
+// SPLIT (the two-wave kernel, this is wave 1): syncs are wave-local and the byte offsets are laid out relative
+// to the delete set's start; then the workgroup's barrier B, after which wave 0's verdict, `hdr` and
+// `struct_bytes` are read from M::L_PUB (the arguments are ignored) and the delete set's start is added while
+// writing.  DS_PRE: declined before barrier B (the caller takes it).
+enum : int { DS_DONE = 0, DS_DECLINE = 1, DS_STOP = 2, DS_PRE = 3 };
+template <class M, uint32_t EE, int STOP, bool DSV2, bool SPLIT = false>
 __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_t nds, uint32_t hdr, uint32_t struct_bytes,
                                         uint64_t slot, uint64_t slot_al, uint64_t slot_end, uint64_t bytes, Slot dst) {
-  const uint32_t lane = threadIdx.x;
+  const uint32_t lane = SPLIT ? threadIdx.x & 63 : threadIdx.x;
   bool bad = false;
     // ---- 5. delete set
     {
@@ -537,7 +610,7 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
         dq[s] = v ? at<uint16_t>(M::L_DSEQ + 2 * i) : 0;
       }
       rank_le4(M::L_DKEY, nds, dk, dr);  // distinct keys: a permutation
-      __syncthreads();
+      lds_sync<SPLIT>();
 #pragma unroll
       for (uint32_t s = 0; s < EE; s++) {
         if (lane + 64 * s < nds) {
@@ -547,7 +620,7 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
           at<uint16_t>(M::L_DSEQ + 2 * r) = (uint16_t)dq[s];
         }
       }
-      __syncthreads();
+      lds_sync<SPLIT>();
     }
     // sorted positions r = E*lane + s: client segments (= groups), running max end of the union,
     // merged ranges.  Per position only its key, end, segment flag and id stay in registers.
@@ -601,7 +674,7 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
       nranges = lane_read(incl_r, 63);
       uint32_t run = incl_r - nr_lane;
       const uint32_t next_first = from_next_lane(newr[0]);  // newr of position E*(lane+1)
-      __syncthreads();  // the sorted delete ranges are in registers (the phase-5 arrays overlay the document bytes)
+      lds_sync<SPLIT>();  // the sorted delete ranges are in registers (the phase-5 arrays overlay the document bytes)
 #pragma unroll
       for (uint32_t s = 0; s < EE; s++) {
         const uint32_t r = r0 + s;
@@ -625,8 +698,8 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
         }
       }
       if (lane == 0) at<uint16_t>(M::L_GFIRST + 2 * ngroups) = (uint16_t)nranges;
-      if (__any(bad)) return DS_DECLINE;
-      __syncthreads();
+      if (__any(bad)) return SPLIT ? DS_PRE : DS_DECLINE;
+      lds_sync<SPLIT>();
       // first appearance of each client: min over its entries' (update << 8 | position)
 #pragma unroll
       for (uint32_t s = 0; s < EE; s++)
@@ -658,7 +731,7 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
       }
       if (lane == 63) at<uint16_t>(M::L_QPRE + 2 * nranges) = (uint16_t)incl;
     }
-    __syncthreads();
+    lds_sync<SPLIT>();
     // groups g = lane + 64 s: bytes and rank by first appearance
     uint32_t grk[EE], gbytes[EE];
 #pragma unroll
@@ -677,9 +750,9 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
 #pragma unroll
     for (uint32_t s = 0; s < EE; s++)
       if (lane + 64 * s < ngroups) at<uint16_t>(M::L_GBYR + 2 * grk[s]) = (uint16_t)gbytes[s];
-    __syncthreads();
+    lds_sync<SPLIT>();
     const uint32_t ds_hdr = vsz(ngroups);
-    const uint32_t dsb = hdr + struct_bytes;
+    uint32_t dsb = SPLIT ? 0 : hdr + struct_bytes;
     uint32_t ds_groups_bytes;
     {  // exclusive prefix over ranks (ranks E*lane + s)
       uint32_t v[EE], t = 0;
@@ -688,7 +761,7 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
       const uint32_t incl = wave_incl_add(t);
       ds_groups_bytes = lane_read(incl, 63);
       uint32_t run = incl - t;
-      __syncthreads();
+      lds_sync<SPLIT>();
 #pragma unroll
       for (uint32_t s = 0; s < EE; s++) {
         const uint32_t r = EE * lane + s;
@@ -696,7 +769,7 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
         run += v[s];
       }
     }
-    __syncthreads();
+    lds_sync<SPLIT>();
     // group g's output offset; its ranges' base = offset + header - prefix of its first range
 #pragma unroll
     for (uint32_t s = 0; s < EE; s++) {
@@ -708,7 +781,15 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
         at<uint32_t>(M::L_GB2 + 4 * g) = off + vsz(at<uint32_t>(M::L_GCLI + 4 * g)) + vsz(f1 - f0) - at<uint16_t>(M::L_QPRE + 2 * f0);
       }
     }
-    __syncthreads();
+    lds_sync<SPLIT>();
+    uint32_t add = 0;  // SPLIT: the delete set's start, added to the relative offsets
+    if constexpr (SPLIT) {
+      __syncthreads();  // barrier B
+      const uint32_t verdict = __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_PUB));
+      if (verdict != SP_DONE) return verdict == SP_CAP ? DS_DONE : DS_DECLINE;  // (SP_CAP: wave 0 wrote the status)
+      add = __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_PUB + 4)) + __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_PUB + 8));
+      dsb = add;
+    }
     const uint32_t total = dsb + ds_hdr + ds_groups_bytes;
     if (slot_al + total > slot_end) {
       if (slot_al + total > slot + 2 * bytes + 64) return DS_DECLINE;
@@ -723,12 +804,12 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
     for (uint32_t s = 0; s < EE; s++) {
       const uint32_t g = lane + 64 * s;
       if (g < ngroups)
-        put_vu(dst, put_vu(dst, at<uint32_t>(M::L_GMIN + 4 * g), at<uint32_t>(M::L_GCLI + 4 * g)),
+        put_vu(dst, put_vu(dst, at<uint32_t>(M::L_GMIN + 4 * g) + add, at<uint32_t>(M::L_GCLI + 4 * g)),
                at<uint16_t>(M::L_GFIRST + 2 * g + 2) - at<uint16_t>(M::L_GFIRST + 2 * g));
       const uint32_t q = EE * lane + s;
       if (q < nranges) {
         const uint32_t c0 = at<uint32_t>(M::L_QCLK + 4 * q);
-        const uint32_t off = at<uint32_t>(M::L_GB2 + 4 * at<uint8_t>(M::L_QGRP + q)) + at<uint16_t>(M::L_QPRE + 2 * q);
+        const uint32_t off = at<uint32_t>(M::L_GB2 + 4 * at<uint8_t>(M::L_QGRP + q)) + at<uint16_t>(M::L_QPRE + 2 * q) + add;
         if constexpr (DSV2) {
           const bool first = at<uint16_t>(M::L_GFIRST + 2 * at<uint8_t>(M::L_QGRP + q)) == q;
           const uint32_t pe = first ? 0 : at<uint32_t>(M::L_QEND + 4 * (q - 1));
@@ -750,21 +831,26 @@ __device__ __forceinline__ int ds_phase(const GeneralJob &j, uint32_t d, uint32_
 // lane, waited for it, stored it, then issued the next): its update offsets (<= 129: three per lane) with the
 // offsets of its first and last byte, then its 16-byte vectors covering [b0, b0 + bytes) (byte b0 lands at LDS
 // offset b0 & 15), then the LDS stores.  False: the document is outside this kernel's shape (declined).
-template <class M, bool DSONLY, class T>
+template <class M, bool DSONLY, uint32_t NT = 64, class T>
 __device__ __forceinline__ bool stage_doc(const GeneralJob &j, const T *off, uint32_t u0, uint32_t k, uint64_t &b0,
                                           uint64_t &bytes, uint64_t &arena0) {
   const uint32_t lane = threadIdx.x;
   arena0 = off[0];  // (the slot's origin, needed after the walk: loaded with the rest, not in the middle of the wave)
-  constexpr uint32_t NO = (UPD + 1 + 63) / 64, NV = (M::IN + 31) / 16 / 64 + 1;
+  constexpr uint32_t NO = (UPD + 1 + NT - 1) / NT, NV = (M::IN + 31) / 16 / NT + 1;
   // (the loads are unconditional, at clamped indices: exec-masked loads made the compiler wait for each one)
   const uint32_t kc = k <= UPD ? k : 0;
   uint64_t ov[NO];
 #pragma unroll
-  for (uint32_t t = 0; t < NO; t++) ov[t] = off[u0 + (lane + 64 * t < kc ? lane + 64 * t : kc)];
+  for (uint32_t t = 0; t < NO; t++) ov[t] = off[u0 + (lane + NT * t < kc ? lane + NT * t : kc)];
 #ifdef YM_STAGE_SCALAR_B0
-  b0 = off[u0];
-  bytes = (uint64_t)off[u0 + k] - b0;
+  constexpr bool SCALAR_B0 = true;
 #else
+  constexpr bool SCALAR_B0 = NT != 64;  // (more than one wave: no lane holds them for all)
+#endif
+  if constexpr (SCALAR_B0) {
+    b0 = off[u0];
+    bytes = (uint64_t)off[u0 + kc] - b0;
+  } else
   // the document's first and last offsets from those loads (lane 0 / the lane holding index kc): one memory
   // round trip for all of them instead of a scalar one first
   {
@@ -774,7 +860,6 @@ __device__ __forceinline__ bool stage_doc(const GeneralJob &j, const T *off, uin
     b0 = lane_read64(ov[0], 0);
     bytes = lane_read64(ve, (int)(kc & 63)) - b0;
   }
-#endif
   if ((DSONLY ? k == 0 : k <= 1) || k > UPD || bytes > M::IN) return false;
   const uint32_t base = (uint32_t)(b0 & 15);
   const uint4 *src = reinterpret_cast<const uint4 *>(j.A + (b0 - base));
@@ -788,7 +873,7 @@ __device__ __forceinline__ bool stage_doc(const GeneralJob &j, const T *off, uin
     uint4 vv[NV];
 #pragma unroll
     for (uint32_t t = 0; t < NV; t++) {
-      vi[t] = lane + 64 * t < nvec ? lane + 64 * t : nvec - 1;
+      vi[t] = lane + NT * t < nvec ? lane + NT * t : nvec - 1;
       vv[t] = src[vi[t]];
     }
 #pragma unroll
@@ -796,7 +881,7 @@ __device__ __forceinline__ bool stage_doc(const GeneralJob &j, const T *off, uin
   }
 #pragma unroll
   for (uint32_t t = 0; t < NO; t++)
-    at<uint16_t>(M::L_UOFF + 2 * (lane + 64 * t < kc ? lane + 64 * t : kc)) = (uint16_t)(ov[t] - b0 + base);
+    at<uint16_t>(M::L_UOFF + 2 * (lane + NT * t < kc ? lane + NT * t : kc)) = (uint16_t)(ov[t] - b0 + base);
   return true;
 }
 
@@ -962,6 +1047,164 @@ __device__ __forceinline__ void merge_doc_v1(const GeneralJob &j, uint32_t di) {
     __syncthreads();
   }
 }
+// The hot V1 merge of document d by a two-wave workgroup (128 threads): after the staging by all 128 lanes, wave
+// 0 runs the struct half (W1 over the first 64 updates with structs, section sort, layout, struct bytes) and
+// wave 1 the delete-set half (W2, union, delete-set bytes), which are independent computations over the staged
+// bytes that meet at the workgroup's barriers:
+//   S  the document's bytes and update offsets are in LDS; each thread then classifies one update (structs /
+//      delete-only with clients) and S2, right behind it, exchanges the two waves' counts and walk lists;
+//   A  every walk is done: wave 1 took W2 over the delete-only updates (their delete sets start at a known
+//      byte) and W1 over the updates with structs beyond the 64th (records through the same LDS counter);
+//      after it wave 1 walks the non-empty delete sets of the updates with structs (L_UDS and the list
+//      L_UORD3 from W1; none in C2) and wave 0 starts the section phase;
+//   B  wave 0 has laid out the struct section and publishes its verdict, `hdr` and `struct_bytes` (L_PUB): wave
+//      1, whose byte offsets are relative to the delete set's start until then, checks the total against the
+//      slot, writes the delete set and the document's result while wave 0 writes the struct bytes.
+// Every wave reaches every barrier: a half that declines skips its remaining work (`dead`), and after B lane 0
+// of wave 1 alone declines the document or writes its result.  The outcome follows the one-wave kernel's order
+// of checks: a struct walk's decline (either wave: L_W1BAD) precedes everything, wave 0's ST_CAPACITY precedes
+// any decline of the delete-set half.  Inside a half all syncs are wave-local (wave_sync).
+template <class M>
+__device__ __forceinline__ void merge_doc_v1_split(const GeneralJob &j, uint32_t d) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t u0 = j.doc_upd[d], k = j.doc_upd[d + 1] - u0;
+  // ---- 1. stage, 128 lanes
+  uint64_t b0 = 0, bytes = 0, arena0 = 0;
+  const bool staged = j.upd_off32 ? stage_doc<M, false, 128>(j, j.upd_off32, u0, k, b0, bytes, arena0)
+                                  : stage_doc<M, false, 128>(j, j.upd_off, u0, k, b0, bytes, arena0);
+  if (!staged) {  // (workgroup-uniform, before any barrier)
+    if (tid == 0) decline(j, d);
+    return;
+  }
+  if (tid < 8) at<uint32_t>(M::L_MISC + 4 * tid) = 0;  // counters, duplicate-check bitmap
+  if (tid < 4) at<uint32_t>(M::L_PUB + 4 * tid) = 0;
+  __syncthreads();  // barrier S
+  // ---- update tables, one update per thread: updates with structs / delete-only updates whose delete set has
+  // clients, each kind compacted per wave into its half of the walk lists; the counts cross at barrier S2
+  uint32_t n1, n2, c0, e0;  // updates with structs, delete-only updates to walk; of those, in wave 0's half
+  bool dead;
+  {
+    bool has = false, hds = false, empty = false;
+    if (tid < k) {
+      const uint32_t u0_ = at<uint16_t>(M::L_UOFF + 2 * tid), ue = at<uint16_t>(M::L_UOFF + 2 * tid + 2);
+      empty = ue == u0_;
+      if (ue != u0_ && sm[u0_] == 0) {
+        // no structs: the delete set follows
+        at<uint16_t>(M::L_UDS + 2 * tid) = (uint16_t)(u0_ + 1);
+        hds = u0_ + 1 >= ue || sm[u0_ + 1] != 0;  // (a missing delete set: W2 declines)
+      } else {
+        has = true;
+      }
+    }
+    const uint64_t hm = __ballot(has), dm = __ballot(hds);
+    if (has) at<uint8_t>(M::L_UORD + 64 * wv + lanes_below(hm)) = (uint8_t)tid;
+    if (hds) at<uint8_t>(M::L_UORD2 + 64 * wv + lanes_below(dm)) = (uint8_t)tid;
+    const uint32_t mine = (uint32_t)__popcll(hm) | ((uint32_t)__popcll(dm) << 8) | (__any(empty) ? 1u << 16 : 0u);
+    if (lane == 0) at<uint32_t>(M::L_TAB + 4 * wv) = mine;
+    __syncthreads();  // barrier S2
+    const uint32_t t0 = __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_TAB)), t1 = __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_TAB + 4));
+    c0 = t0 & 0xffu;
+    e0 = (t0 >> 8) & 0xffu;
+    n1 = c0 + (t1 & 0xffu);
+    n2 = e0 + ((t1 >> 8) & 0xffu);
+    dead = ((t0 | t1) >> 16) != 0;  // an empty update (the same in both waves)
+  }
+  // output slot: 64-aligned inside the bound 2 * in + 64 per doc (no global atomics); worked out by each wave
+  // after its walks (not live across them)
+#define YM_SPLIT_SLOT()                                                                                     \
+  const uint64_t slot = 2 * (b0 - arena0) + 64ull * (d + j.doc_base);                                        \
+  const uint64_t slot_al = (slot + 63) & ~63ull;                                                             \
+  const uint64_t slot_end = slot + 2 * bytes + 64 < j.cap ? slot + 2 * bytes + 64 : j.cap;                   \
+  if (slot_al >= slot_end) dead = true;                                                                      \
+  const Slot dst = make_slot(j.out + slot_al, slot_al >= slot_end ? 0u : (uint32_t)(slot_end - slot_al));
+  if (wv == 0) {
+    // ======== wave 0: the struct half
+    if (!dead) {
+      // the lane-th update with structs (the list's halves: c0 from wave 0's updates, then wave 1's)
+      const uint32_t w = at<uint8_t>(M::L_UORD + (lane < c0 ? lane : 64 + lane - c0));
+      bool ok = true;
+      if (lane < n1) ok = walk_sections<M, false, true>(w);
+      if (__any(!ok)) {
+        dead = true;
+        if (lane == 0) at<uint32_t>(M::L_W1BAD) = 1;
+      }
+    }
+    __syncthreads();  // barrier A
+    dead = dead || __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_W1BAD)) != 0;
+    YM_SPLIT_SLOT()
+    // long non-ASCII strings the walks listed: validated by the whole wave
+    if (!dead && !deferred_ok<M::L_HIST, M::L_MISC + 8>()) dead = true;
+    const uint32_t nsec = __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_MISC));
+    if (nsec == 0 || nsec > SEC) dead = true;
+    int r = SP_DECLINE;
+    uint32_t hdr = 0, struct_bytes = 0;
+    if (!dead) {
+      // pad the key array to a multiple of 4 (rank loops read quads; SEC is a multiple of 4)
+      if (lane < 3 && nsec + lane < ((nsec + 3) & ~3u)) at<uint64_t>(M::L_SKEY + 8 * (nsec + lane)) = ~0ull;
+      wave_sync();
+      r = nsec <= 64 ? sec_phase<M, 1, 0, true>(j, d, nsec, slot, slot_al, slot_end, bytes, dst, hdr, struct_bytes)
+                     : sec_phase<M, 2, 0, true>(j, d, nsec, slot, slot_al, slot_end, bytes, dst, hdr, struct_bytes);
+    }
+    if (r != SP_DONE) {
+      if (lane == 0) at<uint32_t>(M::L_PUB) = (uint32_t)r;
+      __syncthreads();  // barrier B
+    }
+  } else {
+    // ======== wave 1: the delete-set half
+    if (!dead) {
+      bool ok = true;
+#pragma unroll 1
+      for (uint32_t i = lane; i < n2; i += 64) ok &= walk_ds<M>(at<uint8_t>(M::L_UORD2 + (i < e0 ? i : 64 + i - e0)));
+      if (__any(!ok)) dead = true;
+      // the updates with structs that wave 0's lanes do not cover (at most 64: k <= 128; all in wave 1's half of
+      // the list, since c0 <= 64)
+      if (n1 > 64) {
+        bool ok1 = true;
+        if (lane + 64 < n1) ok1 = walk_sections<M, false, true>(at<uint8_t>(M::L_UORD + 128 + lane - c0));
+        if (__any(!ok1) && lane == 0) at<uint32_t>(M::L_W1BAD) = 1;
+      }
+    }
+    __syncthreads();  // barrier A
+    dead = dead || __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_W1BAD)) != 0;
+    YM_SPLIT_SLOT()
+    if (!dead) {
+      // the delete sets of the updates with structs (they start where W1 ended): those with clients, listed by
+      // the struct walks (walk_sections LIST)
+      const uint32_t n3 = __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_MISC + 12));
+      if (n3 != 0) {
+        bool ok = true;
+#pragma unroll 1
+        for (uint32_t i = lane; i < n3; i += 64) ok &= walk_ds<M>(at<uint8_t>(M::L_UORD3 + i));
+        if (__any(!ok)) dead = true;
+      }
+    }
+    wave_sync();
+    const uint32_t nds = __builtin_amdgcn_readfirstlane(at<uint32_t>(M::L_MISC + 4));
+    if (nds > DSN) dead = true;
+    int r = DS_PRE;
+    if (!dead) {
+      if (lane < 3 && nds + lane < ((nds + 3) & ~3u)) at<uint64_t>(M::L_DKEY + 8 * (nds + lane)) = ~0ull;
+      wave_sync();
+      r = nds <= 64 ? ds_phase<M, 1, 0, false, true>(j, d, nds, 0, 0, slot, slot_al, slot_end, bytes, dst)
+                    : ds_phase<M, 2, 0, false, true>(j, d, nds, 0, 0, slot, slot_al, slot_end, bytes, dst);
+    }
+    if (r == DS_PRE) {
+      __syncthreads();  // barrier B
+      // (SP_CAP: wave 0 wrote ST_CAPACITY, which the one-wave kernel reaches before the delete set)
+      if (lane == 0 && at<uint32_t>(M::L_PUB) != SP_CAP) decline(j, d);
+    } else if (r == DS_DECLINE) {
+      if (lane == 0) decline(j, d);
+    }
+  }
+}
+#undef YM_SPLIT_SLOT
+template <int OCC>
+__global__ void __launch_bounds__(128, OCC) k_fast_merge_v1_split(GeneralJob j, uint32_t nd) {
+  const uint32_t d0 = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);  // XCD-contiguous, as below
+  if (d0 < nd) merge_doc_v1_split<MapSplit>(j, d0);
+}
+
 // ONE: the grid covers every document (one per block, no loop: nothing is hoisted across documents, so
 // the per-document values are not kept live -- and spilled -- for the whole kernel); otherwise a
 // grid-stride loop.  Grid: a multiple of 8 blocks; block b takes documents (b % 8) * G/8 + b / 8 + k * G.
@@ -1036,6 +1279,14 @@ int fast_launch(uint32_t op, const GeneralJob &j, uint32_t n_upd, hipStream_t st
   // (the launch bound steers register allocation: 8 keeps the kernel within 8 waves' SGPRs and VGPRs per SIMD,
   // what the 5 KB LDS map allows; 5 lets it use more registers, 7 waves by SGPRs)
   if (occ < 0) { const char *e = getenv("YMERGE_FAST_OCC"); occ = e ? atoi(e) : 8; }
+  // YMERGE_FAST_SPLIT=0: the one-wave kernel instead of the two-wave one (A/B from one library); the ablation
+  // (YMERGE_FAST_STOP) and occupancy (YMERGE_FAST_OCC) builds exist in the one-wave form only
+  static int split = -1;
+  if (split < 0) { const char *e = getenv("YMERGE_FAST_SPLIT"); split = e && atoi(e) == 0 ? 0 : 1; }
+  if (split && stop == 0 && occ == 8 && j.n <= FAST_ONE_MAX) {
+    k_fast_merge_v1_split<8><<<grid, 128, MapSplit::LDS_BYTES + 2 * pad, st>>>(j, j.n);
+    return 1;
+  }
 #define YM_LAUNCH(S, O) k_fast_merge_v1<S, O><<<grid, 64, LDS_BYTES, st>>>(j, j.n)
   if (j.n > FAST_ONE_MAX) {
     k_fast_merge_v1<0, 5, false, false, false, false><<<grid, 64, LDS_BYTES, st>>>(j, j.n);

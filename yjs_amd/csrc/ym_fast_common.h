@@ -47,6 +47,10 @@ __device__ __forceinline__ uint32_t wave_incl_add(uint32_t x) {
   x += YM_DPP(x, 0x143, 0xc);  // row_bcast:31 -> rows 2, 3
   return x;
 }
+// number of set bits of the wave mask m below this lane (v_mbcnt: no per-lane mask register)
+__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
 __device__ __forceinline__ uint32_t lane_read(uint32_t x, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, l); }
 // inclusive prefix max over the 64 lanes, u64
 template <int CTL, int RM>
@@ -70,6 +74,21 @@ __device__ __forceinline__ uint64_t lane_read64(uint64_t x, int l) {
 // value of lane-1 (0 for lane 0) / lane+1 (0 for lane 63): DPP wave_shr:1 / wave_shl:1
 __device__ __forceinline__ uint32_t from_prev_lane(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x138, 0xf, 0xf, false); }
 __device__ __forceinline__ uint32_t from_next_lane(uint32_t x) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x130, 0xf, 0xf, false); }
+
+// Orders the LDS accesses of one wave's lanes around it: a wave's LDS operations complete in issue order, so
+// lanes exchanging data through LDS inside one wave need the compiler not to move accesses across this point and
+// no s_barrier.  lds_sync<false> is the workgroup barrier (no instruction at all in a one-wave block);
+// lds_sync<true> is for code that runs in one wave of a larger block and must not wait for the others.
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+template <bool WAVE>
+__device__ __forceinline__ void lds_sync() {
+  if constexpr (WAVE) wave_sync();
+  else __syncthreads();
+}
 
 // bytes of lib0 writeVarUint(v) for a u32: ceil(significant bits / 7), at least 1 (x * 37 >> 8 == x / 7
 // for x <= 38)
